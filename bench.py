@@ -1,6 +1,7 @@
 """ResNet-18 TQ (g=8, alpha=k=12, wb=db=9, dt=3) inference throughput on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256] [--dump-outputs DIR]
+                    [--full]
         (N > 1 without a launcher: bench.py starts N fresh rank processes itself, before any
         GPU call, rendezvous on 127.0.0.1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -13,10 +14,16 @@ kernels with BN/residual/ReLU/next-layer TR in their epilogue; avgpool and fc ar
 the same stream.  By default each batch is split into two 128-image chunks on two HIP
 streams, launched layer by layer round-robin and replayed as one captured hipGraph, so one
 chunk's kernels fill the CUs the other's leave idle while they drain (bit-identical logits;
---streams 1 --launch eager is the plain one-stream loop).  The kernel rooflines come from a
-separate one-stream pass with full-batch launches.  Inputs are resident in HBM before timing.  Ranks run independent batches (weak
-scaling, no data-path collective); one all-reduce of the accuracy counters closes the
-timed region.  Rank 0 prints one JSON line.
+--streams 1 --launch eager is the plain one-stream loop).  Inputs are resident in HBM before
+timing.  Ranks run independent batches (weak scaling, no data-path collective); one
+all-reduce of the accuracy counters closes the timed region.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline (value,
+ms_per_step, ...).  --dump-outputs DIR also writes what the last timed step computed
+(DIR/logits.npy, DIR/accuracy_counters.npy; rank 0).  --full adds everything else, each from
+runs of its own after the timed region: the kernel rooflines (a separate one-stream pass with
+full-batch launches), the other stems' legs, the TR op alone (d1), LSTM-650 / MobileNet-V2 /
+EfficientNet-b0 (d4) and the CPU baselines (the --no-* options skip single legs of it).
 """
 import argparse
 import json
@@ -63,9 +70,17 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as "
+                         "DIR/<name>.npy (rank 0): logits (float32, batch x 1000) and "
+                         "accuracy_counters (float64: correct, seen over the timed steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the kernel-roofline pass, the other "
+                         "stems' legs, d1, d4 and the CPU baselines (see --no-*)")
     ap.add_argument("--cpu-sample", type=int, default=256,
                     help="images in the CPU-baseline sample (rank 0, N=1 only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baselines")
     ap.add_argument("--engine", choices=("mfma", "valu"), default="mfma",
                     help="term-pair engine: MFMA (fp16 codes) or VALU (int16 codes, "
                          "v_dot2c_i32_i16); bit-identical outputs")
@@ -80,9 +95,9 @@ def parse(argv=None):
                          "each kernel's drain overlaps the other chunk's kernel; 1 = one "
                          "stream)")
     ap.add_argument("--no-d1", action="store_true",
-                    help="skip the d1_tr_op key (SURVEY 8(d) D1: the TR op alone)")
+                    help="with --full: skip the d1_tr_op key (SURVEY 8(d) D1: the TR op alone)")
     ap.add_argument("--no-d4", action="store_true",
-                    help="skip the d4 key (BASELINE configs[2]/[3]: LSTM-650, fused "
+                    help="with --full: skip the d4 key (BASELINE configs[2]/[3]: LSTM-650, fused "
                          "MobileNet-V2 / EfficientNet-b0; rank 0 at N=1 only)")
     ap.add_argument("--stem", choices=("fused", "exact", "fp32"), default="exact",
                     help="exact: the fused stem kernel (split-fp16 MFMA conv) + its exact "
@@ -90,7 +105,7 @@ def parse(argv=None):
                          "fused stem kernel alone (near-fp32); fp32: torch's fp32 conv + the "
                          "BN/ReLU/max-pool/codes kernel")
     ap.add_argument("--no-stem-leg", action="store_true",
-                    help="skip the second timed pass with the other stem (N=1 only)")
+                    help="with --full: skip the timed passes with the other stems (N=1 only)")
     ap.add_argument("--unfused", action="store_true",
                     help="run the module path (separate BN/ReLU/add/TR passes) instead of "
                          "the fused executor")
@@ -438,6 +453,16 @@ def d1_tr_op(dev, iters=20):
             "hbm_frac": gbs / HBM_PEAK_GBS, "bytes_per_element": 8, "launches": iters}
 
 
+def dump_outputs(path, logits, counters):
+    """--dump-outputs: what the last timed step handed back, one .npy per array -- the logits
+    of its batch (float32, whole: batch x 1000 is ~1 MB) and the accuracy counters (correct,
+    seen) the steps accumulated.  The model, its calibration and the resident batches are
+    seeded, so two runs with the same arguments write comparable files."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "logits.npy"), logits.numpy().astype(np.float32))
+    np.save(os.path.join(path, "accuracy_counters.npy"), np.asarray(counters, dtype=np.float64))
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse(argv)
@@ -481,12 +506,16 @@ def main(argv=None):
 
     def timed_steps(runner):
         """W untimed warmup steps, (optionally) one hipGraph per resident batch, then the K
-        timed steps between barrier + synchronize: (seconds, launch mode, counters)."""
+        timed steps between barrier + synchronize: (seconds, launch mode, counters, the
+        last step's logits -- read back after the timed region)."""
+        outs = [None, None]  # the logits of the latest step on each resident batch
+
         def step(i):
             x, y = batches[i % 2]
             out = runner(x) if streams is None else runner.forward_streams(x, streams)
             counters[0] += (out.argmax(1) == y).sum()
             counters[1] += y.numel()
+            outs[i % 2] = out  # under capture: the graph's own output buffer
 
         for i in range(args.warmup):
             step(i)
@@ -528,11 +557,13 @@ def main(argv=None):
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
-        return time.perf_counter() - t0, launch, [int(v) for v in counters.tolist()]
+        elapsed = time.perf_counter() - t0
+        # the last step ran batch (K - 1) % 2 (K = 0: the untimed first replays ended on 1)
+        last = outs[(args.steps - 1) % 2 if args.steps > 0 else 1]
+        return elapsed, launch, [int(v) for v in counters.tolist()], last.float().cpu()
 
-    with torch.no_grad():
-        elapsed, launch, acc_counters = timed_steps(runner)
-
+    def full_passes():
+        """--full: the kernel-roofline pass and the other stems' legs, after the headline."""
         # Kernel roofline pass: the same K steps again, eager, with HIP events around every
         # TQ kernel on its launch stream (events between kernels cost ~10 us of idle GPU
         # each, so they stay out of the timed region above).
@@ -559,11 +590,20 @@ def main(argv=None):
             for other in ("fp32", "exact", "fused"):
                 if other == args.stem:
                     continue
-                el2, launch2, _ = timed_steps(tq_fuse.FusedResNet(qmodel, stem=other))
+                el2, launch2, _, _ = timed_steps(tq_fuse.FusedResNet(qmodel, stem=other))
                 stem_legs["stem_" + other] = {
                     "stem": STEM_NAMES[other], "images_per_s": args.batch * args.steps / el2,
                     "ms_per_step": el2 / args.steps * 1e3, "launch": launch2,
                     "streams": args.streams}
+        return timer.summary(), roof_pass_s, stem_legs
+
+    kt, roof_pass_s, stem_legs = None, None, {}
+    with torch.no_grad():
+        elapsed, launch, acc_counters, last_logits = timed_steps(runner)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last_logits, acc_counters)
+        if args.full:
+            kt, roof_pass_s, stem_legs = full_passes()
 
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if world > 1:
@@ -571,10 +611,13 @@ def main(argv=None):
     elapsed = float(t.item())
     images = args.batch * args.steps * world
     ips = images / elapsed
-    kt = timer.summary()
 
     result = None
-    if rank == 0:
+    mfma = args.engine == "mfma"
+    # the stem the step ran: the fused stem kernel (--stem fused / exact) or torch's fp32 conv
+    fused_stem = getattr(runner, "stem_w", None) is not None
+    roof = roof_tr = None
+    if rank == 0 and args.full:
         conv = kt["conv2d_termpair"]
         # the HBM-bound TR stage of the step: the fused stem tail (BN/ReLU/max-pool + the
         # first TR layer's activation TR) in the fused executor, act_encode otherwise
@@ -589,7 +632,6 @@ def main(argv=None):
         enc_t = enc["busy"] / enc["launches"]
         enc_bytes = enc["work"] / enc["launches"]
         traffic = enc_traffic = None
-        mfma = args.engine == "mfma"
         pmc_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
         if os.path.exists(pmc_path):
             pmc = json.load(open(pmc_path))
@@ -693,6 +735,8 @@ def main(argv=None):
                 "avg_launch_us": enc_t * 1e6,
                 "launches": enc["launches"],
             }
+        fused_stem = enc_name == "stem_conv_pool"
+    if rank == 0:
         result = {
             "metric": METRIC,
             "value": ips,
@@ -721,7 +765,7 @@ def main(argv=None):
                        # the fused stem kernel as a split-fp16 conv with the exact fix-up
                        # (default: correctly rounded codes), without it (--stem fused), or
                        # (--stem fp32) as torch's fp32 conv
-                       "stem": STEM_NAMES[args.stem if enc_name == "stem_conv_pool" else "fp32"]},
+                       "stem": STEM_NAMES[args.stem if fused_stem else "fp32"]},
             "term_pair_macs_per_image": tmacs_per_img,
             "term_pair_macs_per_s": tmacs_per_img * ips,
             "roofline": roof,
@@ -729,13 +773,15 @@ def main(argv=None):
             "accuracy_counters": acc_counters,
         }
         result.update(stem_legs)
-        if world == 1 and not args.no_d1:
+        if not args.full:  # the rooflines come from --full's pass of their own
+            del result["roofline"], result["roofline_tr"]
+        if args.full and world == 1 and not args.no_d1:
             result["d1_tr_op"] = d1_tr_op(dev)
-        if world == 1 and not args.no_d4:
+        if args.full and world == 1 and not args.no_d4:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import bench_d4
             result["d4"] = bench_d4.d4_summary(dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(model_fp, qmodel, args.cpu_sample)
     if world > 1:
         dist.barrier()

@@ -103,3 +103,26 @@ def test_check_world_counts_this_nodes_ranks(monkeypatch):
     assert bench.check_world(8, 3)
     assert not bench.check_world(9, 3)
     assert not bench.check_world(4, 8)
+
+
+def test_plain_run_is_the_default_and_full_is_an_option():
+    """A plain run carries none of the extra legs: --full is off unless asked for, and
+    --dump-outputs names the directory of the .npy files."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float_npy(tmp_path):
+    """--dump-outputs: one .npy per array, float32 logits and float64 counters, values kept."""
+    import numpy as np
+    import torch
+    logits = torch.arange(12, dtype=torch.float32).view(3, 4) / 7
+    d = tmp_path / "out" / "dump"
+    bench.dump_outputs(str(d), logits, [5, 768])
+    assert sorted(p.name for p in d.iterdir()) == ["accuracy_counters.npy", "logits.npy"]
+    got = np.load(str(d / "logits.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, logits.numpy())
+    c = np.load(str(d / "accuracy_counters.npy"))
+    assert c.dtype == np.float64 and c.tolist() == [5.0, 768.0]

@@ -8,7 +8,7 @@ timeout -k 10 600 python -u -m pytest $TESTS -x -q --timeout 300 --timeout-metho
 rc=$?; tail -2 $O/tests.log; [ $rc -ne 0 ] && exit $rc
 for r in 1 2; do for v in new old; do
   L=$PWD/term-quantization_amd/lib/libtq_hip.so; [ $v = old ] && L=$OLD
-  TQ_LIB_PATH=$L timeout -k 10 400 python3 bench.py --no-d1 --no-cpu-baseline --no-stem-leg > $O/b_${v}_$r.json 2> $O/b_${v}_$r.err
+  TQ_LIB_PATH=$L timeout -k 10 400 python3 bench.py --full --no-d1 --no-cpu-baseline --no-stem-leg > $O/b_${v}_$r.json 2> $O/b_${v}_$r.err
   rc=$?; [ $rc -ne 0 ] && { tail -5 $O/b_${v}_$r.err; exit $rc; }
   python3 -c "
 import json; d=json.loads(open('$O/b_${v}_$r.json').read().strip().splitlines()[-1]); d4=d['d4']

@@ -14,7 +14,7 @@ for v in new old; do
 done
 for r in 1 2 3; do for v in new old; do
   L=$PWD/term-quantization_amd/lib/libtq_hip.so; [ $v = old ] && L=$OLD
-  TQ_LIB_PATH=$L timeout -k 10 300 python3 bench.py --stem exact --no-d4 --no-d1 --no-cpu-baseline --no-stem-leg > $O/b_${v}_$r.json 2> $O/b_${v}_$r.err
+  TQ_LIB_PATH=$L timeout -k 10 300 python3 bench.py --full --stem exact --no-d4 --no-d1 --no-cpu-baseline --no-stem-leg > $O/b_${v}_$r.json 2> $O/b_${v}_$r.err
   rc=$?; [ $rc -ne 0 ] && { tail -5 $O/b_${v}_$r.err; exit $rc; }
   python3 -c "import json; d=json.loads(open('$O/b_${v}_$r.json').read().strip().splitlines()[-1]); print('$v', round(d['value']), round(d['ms_per_step'],4), 'conv', round(d['roofline']['avg_launch_us'],2), 'stem', round(d['roofline_tr']['avg_launch_us'],1))"
 done; done
